@@ -9,8 +9,13 @@ of pairs (seeded by the global pair index), no data-path collective; one RCCL al
 counters at the end.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if `--dump-outputs DIR` is given, and prints the
+headline line.  Every other leg (PCK and conformance records, `sustained`, the episode protocol, the CPU baseline and parity sample,
+the unpipelined / conforming / bf16 comparison runs) runs only with `--full`; the `--no-*` switches choose among them there.
 
 Prints ONE JSON line on rank 0.  `roofline` is for the north-star kernel (backbone QKV GEMM, its own
 kernel symbol gemm8_bf16_kernel<1, 1, ..>): algorithmic FLOPs per launch / mean launch duration measured with
@@ -68,6 +73,14 @@ def parse():
     ap.add_argument("--no-pipeline", action="store_true",
                     help="time ec_forward (every call complete at its own end) instead of ec_forward_pipelined (the decoder phase of "
                          "step i runs beside the backbone of step i+1; all work of the K steps still lies inside the timed region)")
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg beside the headline as well: PCK vs the synthetic ground truth, the conformance records, "
+                         "`sustained`, the episode protocol, the CPU baseline + parity sample and the comparison runs (the --no-* "
+                         "switches above choose among them).  Off: only the headline's warm-up and K timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed step (rank 0's shard; what forward_test's device "
+                         "part hands its caller) as DIR/<name>.npy in float32, at most 64 MB in all (a fixed, seeded sample of the "
+                         "pairs beyond that)")
     return ap.parse_args()
 
 
@@ -153,22 +166,26 @@ def main():
     qkv_flops = 2.0 * Mq * Kq * Nq
     achieved = qkv_flops / (qkv_ms * 1e-3) / 1e12 if qkv_ms > 0 else 0.0
     peak = PEAK_TFLOPS[args.precision]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs[0])
 
-    # ---- accuracy bookkeeping on this rank's last outputs: PCK vs the synthetic ground truth (random weights: chance level; the
-    # meaningful agreement figures are in `parity_sample`: HIP predictions against the oracle's on the same pairs)
-    out_k = outputs[0]["output_kpts"][-1].cpu().numpy()            # [bs,K,2] normalised
-    scale200 = np.stack([m["query_scale"] for m in batch["img_metas"]]) * 200.0
-    center = np.stack([m["query_center"] for m in batch["img_metas"]])
-    pred_px = out_k * H * (scale200 / H)[:, None, :] + center[:, None, :] - scale200[:, None, :] * 0.5
-    vis = (mask[:, :, 0] > 0) & (batch["target_weight_q"][:, :, 0] > 0)
-    norm = np.full((bs, 2), float(H))
-    counts = pck_counts(pred_px, batch["gt_q"], vis, norm)
-    counts = apis.allreduce_counts(counts)
-    pck = pck_from_counts(counts)
+    pck = None
+    if args.full:
+        # ---- accuracy bookkeeping on this rank's last outputs: PCK vs the synthetic ground truth (random weights: chance level; the
+        # meaningful agreement figures are in `parity_sample`: HIP predictions against the oracle's on the same pairs)
+        out_k = outputs[0]["output_kpts"][-1].cpu().numpy()            # [bs,K,2] normalised
+        scale200 = np.stack([m["query_scale"] for m in batch["img_metas"]]) * 200.0
+        center = np.stack([m["query_center"] for m in batch["img_metas"]])
+        pred_px = out_k * H * (scale200 / H)[:, None, :] + center[:, None, :] - scale200[:, None, :] * 0.5
+        vis = (mask[:, :, 0] > 0) & (batch["target_weight_q"][:, :, 0] > 0)
+        norm = np.full((bs, 2), float(H))
+        counts = pck_counts(pred_px, batch["gt_q"], vis, norm)
+        counts = apis.allreduce_counts(counts)
+        pck = pck_from_counts(counts)
 
     # ---- legs that run on EVERY rank (their timed regions carry the same barriers / max over ranks as the headline's)
     sustained = None
-    if args.sustained_seconds > 0 and pipelined:
+    if args.full and args.sustained_seconds > 0 and pipelined:
         n_s = max(args.steps, int(np.ceil(args.sustained_seconds / (dt / args.steps))))
         _, _, dt_s, qkv_s = timed_run(args.precision, n_s, 0, True, True, eng=eng)
         ach_s = qkv_flops / (qkv_s * 1e-3) / 1e12 if qkv_s > 0 else 0.0
@@ -177,7 +194,7 @@ def main():
                      "launches_timed": timed_run.launches,
                      "note": "the same pipelined steps for >= %.0f s in the same process, same engine, right after the K timed steps of `value`" % args.sustained_seconds}
     episode = None
-    if not args.no_episode:
+    if args.full and not args.no_episode:
         episode = episode_mode(args, sd, synth, bs, S, H, arch, apis, rank, world, parity_episodes=0 if args.no_cpu_baseline else 2)
         if not args.episode_images and torch.cuda.is_available():
             # the same protocol in calls of twice the size (288 GB of HBM: the call size is free; the head's ~190 launches per call
@@ -206,12 +223,13 @@ def main():
                                          "the previous step's head" if pipelined else "the timed region of `value`: the K ec_forward steps - nothing else on the chip"),
                          "launch_sampling": "one QKV launch per step bracketed by HIP events on the launch stream, block index = step % depth",
                          **pmc_traffic(args, bs, S, H, arch, build.source_hash())},
-            "pck_vs_synthetic_gt": {k: round(v, 4) for k, v in pck.items()},
             # every switch that changes what the library runs (README "Runtime switches"): none set = the shipped defaults
             "env": {k: v for k, v in sorted(os.environ.items()) if k.startswith("EC_")},
             "library_source_hash": build.source_hash()[:16],
         }
-        conf = conformance_record(args, bs, S, H, arch)
+        if pck is not None:
+            result["pck_vs_synthetic_gt"] = {k: round(v, 4) for k, v in pck.items()}
+        conf = conformance_record(args, bs, S, H, arch) if args.full else None
         if conf:
             result["conformance_at_scale"] = conf
         if sustained:
@@ -219,9 +237,9 @@ def main():
         if episode:
             result["episode_cached"] = episode
             result["episode_cached"]["speedup_vs_value"] = round(episode["value"] / result["value"], 3)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             result["cpu_baseline"], result["parity_sample"] = cpu_baseline(args, sd, eng, synth)
-    if world == 1 and not args.no_alt and pipelined:
+    if args.full and world == 1 and not args.no_alt and pipelined:
         # the same steps through ec_forward (every call complete when the stream reaches its end), measured beside the headline
         del eng, outputs
         torch.cuda.empty_cache()
@@ -240,7 +258,7 @@ def main():
             result["roofline"]["kernel_isolated"] = {
                 "achieved": round(ach_u, 2), "frac": round(ach_u / peak, 4), "avg_launch_ms": round(qkv_u, 5), "launches_timed": timed_run.launches,
                 "measured_in": f"{n_u} timed ec_forward steps of this process (nothing else on the chip), one sampled launch per step"}
-    if world == 1 and not args.no_alt and (args.precision, args.head_precision) != CONFORMING:
+    if args.full and world == 1 and not args.no_alt and (args.precision, args.head_precision) != CONFORMING:
         # the tolerance-conforming fast mode, same process, same box, same API as the headline.  Round 6: fp16x2 backbone (a_hi W_hi in fp16
         # MFMAs + both correction terms in ONE block-scaled FP8 pass: two MFMA units per product instead of the three of bf16x3) + bf16x3
         # head; meets the 1e-3 coordinate tolerance on every keypoint but the near-ties any GPU summation order flips (0 / 2 / 1 / 1 argmax
@@ -275,7 +293,7 @@ def main():
         eng, outputs, dt_3, qkv_3 = timed_run("bf16x3", n_c, args.warmup, True, pipelined, head_precision="bf16x3")
         result["conforming_mode"]["bf16x3_bf16x3"] = {"value": round(bs * n_c / dt_3, 2), "unit": "images/s", "ms_per_step": round(dt_3 / n_c * 1e3, 3),
                                                       "qkv_launch_ms": round(qkv_3, 5), "note": "round 5's conforming mode: every product as three bf16 MFMAs"}
-    if world == 1 and not args.no_alt and args.precision != "bf16":
+    if args.full and world == 1 and not args.no_alt and args.precision != "bf16":
         # the same step with bf16 operands (north_star's wording): same kernels and rate, 8x coarser rounding - measured beside the
         # headline so both precisions come from one process on one box; it does NOT meet the 1e-3 gate (test_bf16_mode_cfg2_bounded)
         del eng, outputs
@@ -289,6 +307,28 @@ def main():
         print(json.dumps(result), flush=True)
     apis.finalize_distributed()
     return result
+
+
+DUMP_BYTES = 60 << 20                                    # array data --dump-outputs writes at most (64 MB with the .npy headers)
+DUMP_PAIR_AXIS = {"output_kpts": 1, "attn_adj": 1, "out_points": 1}   # the others (engine._outputs) lead with the pair axis
+
+
+def dump_outputs(path, outs, seed=0):
+    """--dump-outputs: every output array of the last timed step as <path>/<name>.npy, float32.  When they exceed DUMP_BYTES together,
+    one fixed, seeded sample of pairs (sorted, drawn from `seed` alone) is kept in every array, so that two builds dump the same entries."""
+    import torch
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    arrs = {k: v.detach().float().cpu().numpy() for k, v in outs.items() if isinstance(v, torch.Tensor)}
+    n = arrs["output_kpts"].shape[DUMP_PAIR_AXIS["output_kpts"]]
+    per_pair = sum(a.nbytes for a in arrs.values()) / n
+    if per_pair * n > DUMP_BYTES:
+        keep = np.sort(np.random.default_rng(seed).choice(n, max(1, int(DUMP_BYTES // per_pair)), replace=False))
+        arrs = {k: np.take(a, keep, axis=DUMP_PAIR_AXIS.get(k, 0)) for k, a in arrs.items()}
+        print(f"[bench] --dump-outputs: {len(keep)} of {n} pairs (seed {seed})", file=sys.stderr)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 CONF_CFG = {(32, 1, 224, "dinov2_vits14"): "cfg1_", (32, 1, 256, "dinov2_vitb14"): "", (16, 5, 256, "dinov2_vitb14"): "cfg4_", (8, 1, 384, "dinov2_vitl14"): "cfg5_"}

@@ -434,7 +434,35 @@ def round5_fixtures():
     variant_fixture(ns, "head_stage2_c384_g16_s2", 384, 16, 2, [17, 0], "auto", 108, learn_skeleton=True)
 
 
+def encode_config(x):
+    """A loaded config as JSON-able data; tuples become {"__tuple__": [...]} so that decode_config gives back the same value."""
+    if isinstance(x, dict):
+        return {k: encode_config(v) for k, v in x.items()}
+    if isinstance(x, tuple):
+        return {"__tuple__": [encode_config(v) for v in x]}
+    if isinstance(x, list):
+        return [encode_config(v) for v in x]
+    assert x is None or isinstance(x, (bool, int, float, str)), type(x)
+    return x
+
+
+def reference_configs_fixture(name="reference_configs"):
+    """The VALUES every configs/{test,train}/*.py of the reference evaluates to (edgecape_amd.Config.fromfile, i.e. runpy), keyed by
+    the file's path relative to the reference root: tests/test_reference_configs.py builds the model from each of them."""
+    import glob
+    from edgecape_amd import Config
+    cfgs = {}
+    for sub in ("test", "train"):
+        for path in sorted(glob.glob(os.path.join(ref_stubs.REF_ROOT, "configs", sub, "*.py"))):
+            cfgs[os.path.relpath(path, ref_stubs.REF_ROOT)] = encode_config(dict(Config.fromfile(path)._cfg))
+    assert cfgs, f"no configs under {ref_stubs.REF_ROOT}/configs"
+    save(name, {}, {"configs": cfgs, "source": "Config.fromfile(<reference>/configs/{test,train}/*.py)"})
+
+
 def main():
+    if "--configs" in sys.argv:         # the reference's config files as data (tests/test_reference_configs.py)
+        reference_configs_fixture()
+        return
     if "--round5" in sys.argv:
         torch.manual_seed(0)
         torch.set_num_threads(8)

@@ -227,7 +227,7 @@ def _worker_bench(rank, world, port, q):
     engine.HipEngine = _FakeEngine
     import bench
     sys.argv = ["bench.py", "--gpus", str(world), "--steps", "3", "--warmup", "1", "--batch", "4", "--image-size", "56", "--arch", "dinov2_vits14",
-                "--sustained-seconds", "0.05"]
+                "--full", "--sustained-seconds", "0.05"]
     buf = io.StringIO()
     with redirect_stdout(buf):
         res = bench.main()
@@ -266,6 +266,70 @@ def test_world2_bench_main_runs_its_distributed_branches():
     assert "parity_sample" not in epi                           # the episode leg's oracle sample (round 6) is an N = 1, rank-0-only leg as well
     assert res0["pipelined"] is True and "unpipelined" not in res0
     assert set(res0["pck_vs_synthetic_gt"]) >= {"PCK@0.2"}
+
+
+def test_plain_bench_main_is_the_headline_alone(tmp_path, monkeypatch):
+    """bench.py main() without --full (world size 1, the stand-in engine on CPU): one engine, the warm-up and K timed steps and no other
+    leg; --dump-outputs writes the last timed step's outputs (the stand-in's keypoints: 0.5 + 0.1 * mean of the query image) as float32."""
+    import torch
+    import edgecape_amd.engine as engine
+    import bench
+    from edgecape_amd import synth
+    made = []
+
+    class _Counted(_FakeEngine):
+        def __init__(self, *a, **kw):
+            super().__init__(*a, **kw)
+            made.append(self)
+
+    monkeypatch.setattr(engine, "HipEngine", _Counted)
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2", "--batch", "4", "--image-size", "56",
+                                      "--arch", "dinov2_vits14", "--dump-outputs", str(tmp_path / "out")])
+    res = bench.main()
+    assert len(made) == 1 and made[0].calls == 2 + 5 and not hasattr(made[0], "episode_calls")
+    assert res["steps"] == 5 and res["warmup"] == 2 and res["n_gpus"] == 1 and res["roofline"]["launches_timed"] == 5
+    v, ms = res["value"], res["ms_per_step"]                    # both from one timed region, rounded to 0.01 images/s and 1 us
+    assert v > 0 and 4e3 / (v + 0.005) - 0.0005 - 1e-9 <= ms <= 4e3 / (v - 0.005) + 0.0005 + 1e-9
+    assert not {"pck_vs_synthetic_gt", "sustained", "episode_cached", "cpu_baseline", "unpipelined", "conforming_mode", "bf16_mode"} & set(res)
+    assert os.listdir(tmp_path / "out") == ["output_kpts.npy"]
+    got = np.load(tmp_path / "out" / "output_kpts.npy")
+    img_q = synth.make_pairs(4, 1, 56, seed=1000, first_index=0, fixed_n_kp=False)["img_q"]
+    want = 0.5 + 0.1 * img_q.reshape(4, -1).astype(np.float32).mean(1)
+    assert got.dtype == np.float32 and got.shape == (3, 4, 100, 2)
+    np.testing.assert_allclose(got, np.broadcast_to(want[None, :, None, None], got.shape), rtol=1e-5)
+
+
+def test_dump_outputs_keeps_one_seeded_sample_of_pairs(tmp_path, monkeypatch):
+    """bench.dump_outputs over its byte budget: the same sorted sample of pairs in every array, the same in every run, within budget."""
+    import torch
+    import bench
+    bs, K = 10, 6
+    shapes = {"output_kpts": (3, bs, K, 2), "initial_proposals": (bs, K, 2), "similarity_map": (bs, K, 4, 4), "adj": (bs, 2, K, K),
+              "attn_adj": (5, bs, K, K), "out_points": (4, bs, K, 2)}
+    outs = {}
+    for k, shp in shapes.items():
+        ax = bench.DUMP_PAIR_AXIS.get(k, 0)
+        pair = torch.arange(bs, dtype=torch.float64).reshape([bs if i == ax else 1 for i in range(len(shp))])
+        outs[k] = pair.expand(shp).contiguous()                  # every entry holds its pair index (float64: dumped as float32)
+    bench.dump_outputs(str(tmp_path / "all"), outs)
+    for k in shapes:
+        a = np.load(tmp_path / "all" / (k + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, outs[k].numpy())
+    total = sum(int(np.prod(s)) * 4 for s in shapes.values())
+    monkeypatch.setattr(bench, "DUMP_BYTES", total * 3 // 10)
+    kept = []
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), outs)
+        arrs = {k: np.load(tmp_path / run / (k + ".npy")) for k in shapes}
+        assert sum(a.nbytes for a in arrs.values()) <= bench.DUMP_BYTES
+        for k, a in arrs.items():
+            ax = bench.DUMP_PAIR_AXIS.get(k, 0)
+            kept.append(np.moveaxis(a, ax, 0).reshape(a.shape[ax], -1)[:, 0].tolist())
+    assert kept[0] == sorted(kept[0]) and len(kept[0]) == 3 and len(set(kept[0])) == 3
+    assert all(k == kept[0] for k in kept)
 
 
 def test_shard_indices_is_distributed_sampler():

@@ -1,5 +1,6 @@
 """bench.py contract (task prompt section 4): one JSON line on rank 0 with the required keys, run directly and through
-torch.distributed.run with one rank (the driver's launch line), on a small configuration so it finishes in seconds."""
+torch.distributed.run with one rank (the driver's launch line), on a small configuration so it finishes in seconds.  The legs
+beside the headline run with --full; a plain run is the headline alone and can dump its outputs."""
 import json
 import os
 import socket
@@ -9,7 +10,7 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--steps", "3", "--warmup", "1", "--batch", "4", "--arch", "dinov2_vits14", "--image-size", "224", "--no-episode",
+SMALL = ["--steps", "3", "--warmup", "1", "--batch", "4", "--arch", "dinov2_vits14", "--image-size", "224", "--full", "--no-episode",
          "--cpu-batches", "1,4", "--cpu-runs", "1", "--no-alt"]
 REQUIRED = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
             "dtype", "data", "config", "roofline", "cpu_baseline"}
@@ -89,3 +90,33 @@ def test_bench_unpipelined_flag_and_companion_run():
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     assert d["pipelined"] is False and "unpipelined" not in d
+
+
+FULL_ONLY = ("pck_vs_synthetic_gt", "conformance_at_scale", "sustained", "episode_cached", "cpu_baseline", "parity_sample", "unpipelined",
+             "value_reference_contract", "conforming_mode", "bf16_mode")
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """Without --full: the headline's K timed steps and nothing else in the line; --dump-outputs writes the last timed step's outputs."""
+    dump = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4", "--arch", "dinov2_vits14",
+           "--image-size", "224", "--dump-outputs", str(dump)]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["higher_is_better"] is True and d["unit"] == "images/s"
+    assert d["metric"].startswith("query images/sec") and d["dtype"] == "f16" and d["pipelined"] is True
+    assert d["value"] > 0 and abs(d["value"] - 4 * 1e3 / d["ms_per_step"]) / d["value"] < 0.02
+    assert d["roofline"]["launches_timed"] == 3                   # the headline's own sampled QKV launches
+    assert not set(FULL_ONLY) & set(d), set(FULL_ONLY) & set(d)
+    shapes = {"output_kpts": (3, 4, 100, 2), "initial_proposals": (4, 100, 2), "similarity_map": (4, 100, 16, 16), "adj": (4, 2, 100, 100),
+              "attn_adj": (5, 4, 100, 100), "out_points": (4, 4, 100, 2)}
+    assert sorted(os.listdir(dump)) == sorted(k + ".npy" for k in shapes)
+    import numpy as np
+    for k, shp in shapes.items():
+        a = np.load(dump / (k + ".npy"))
+        assert a.dtype == np.float32 and a.shape == shp, (k, a.dtype, a.shape)
+    assert np.isfinite(np.load(dump / "output_kpts.npy")).all()

@@ -56,9 +56,15 @@ def _weights(arch, seed):
 
 # ---- the oracle's answers, computed once per box: the CPU oracle is the expensive half of every test here (5 pairs/s at cfg2), the same
 # batches are asked for by several tests and by every child process of test_runtime_switch_matrix, and the at-scale cases need hundreds
-# of pairs.  Results are cached under /tmp keyed by everything that determines them; missing ones are computed by a
+# of pairs.  Results are cached in the temp dir keyed by everything that determines them; missing ones are computed by a
 # pool of worker processes side by side (the host has far more cores than one eager CPU forward can use).
 ORACLE_KEYS = ("output_kpts", "similarity_map", "adj")
+
+
+def _oracle_cache_dir():
+    """EC_ORACLE_CACHE, else a directory of this user's own under the system temp dir (a shared fixed path fails for a second user)"""
+    import tempfile
+    return os.environ.get("EC_ORACLE_CACHE") or os.path.join(tempfile.gettempdir(), "ec_oracle_cache_%d" % os.getuid())
 
 
 def _oracle_cache_path(name, wseed, seed, first_index, outliers):
@@ -70,7 +76,7 @@ def _oracle_cache_path(name, wseed, seed, first_index, outliers):
             h.update(fh.read())
     c = CFG[name]
     h.update(repr((c["arch"], c["H"], c["bs"], c["S"], wseed, seed, first_index, bool(outliers))).encode())
-    d = os.path.join(os.environ.get("EC_ORACLE_CACHE", "/tmp/ec_oracle_cache"))
+    d = _oracle_cache_dir()
     os.makedirs(d, exist_ok=True)
     return os.path.join(d, h.hexdigest()[:24] + ".npz")
 
@@ -132,7 +138,7 @@ def _oracle_episode_path(name, wseed, n_ep, qpe, chunk, chunk_pairs, outliers=Fa
             h.update(fh.read())
     c = CFG[name]
     h.update(repr(("episodes", c["arch"], c["H"], c["S"], c["iseed"], wseed, n_ep, qpe, chunk, chunk_pairs, bool(outliers))).encode())
-    d = os.path.join(os.environ.get("EC_ORACLE_CACHE", "/tmp/ec_oracle_cache"))
+    d = _oracle_cache_dir()
     os.makedirs(d, exist_ok=True)
     return os.path.join(d, "ep_" + h.hexdigest()[:24] + ".npz")
 

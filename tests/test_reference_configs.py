@@ -1,23 +1,50 @@
 """The boundary claim of SURVEY §8b: every `configs/test/*.py` (and train config) of the reference loads UNCHANGED through
-`edgecape_amd.Config` and builds through the registries under the reference's names.  Reads the reference tree, so it
-runs only where /root/reference is mounted (the build container); it is skipped on the GPU box."""
-import glob
+`edgecape_amd.Config` and builds through the registries under the reference's names.  The configs are the values the reference's
+files evaluate to, stored as data in tests/golden/reference_configs.npz (oracle/make_golden.py --configs); each is written back
+as a plain Python config file and loaded through `Config.fromfile`, as test.py loads the reference's own."""
 import os
 
 import pytest
 
-REF = "/root/reference"
-CONFIGS = sorted(glob.glob(os.path.join(REF, "configs", "test", "*.py")))
-TRAIN = sorted(glob.glob(os.path.join(REF, "configs", "train", "*.py")))
+from conftest import load_golden
 
-pytestmark = pytest.mark.skipif(not CONFIGS, reason="reference tree not mounted")
+_, _META = load_golden("reference_configs")
+CONFIGS = sorted(p for p in _META["configs"] if p.startswith("configs/test/"))
+TRAIN = sorted(p for p in _META["configs"] if p.startswith("configs/train/"))
 
 
-@pytest.mark.parametrize("path", CONFIGS, ids=[os.path.relpath(p, REF) for p in CONFIGS])
-def test_reference_config_builds_unchanged(path):
+def _decode(x):
+    """inverse of oracle/make_golden.py encode_config"""
+    if isinstance(x, dict):
+        if set(x) == {"__tuple__"}:
+            return tuple(_decode(v) for v in x["__tuple__"])
+        return {k: _decode(v) for k, v in x.items()}
+    if isinstance(x, list):
+        return [_decode(v) for v in x]
+    return x
+
+
+def _config_file(rel, tmp_path):
+    """the stored config `rel` as a Python config file of top-level assignments; checks that Config.fromfile gives back its values"""
+    from edgecape_amd import Config
+    values = _decode(_META["configs"][rel])
+    path = tmp_path / os.path.basename(rel)
+    path.write_text("".join(f"{k} = {v!r}\n" for k, v in values.items()))
+    cfg = Config.fromfile(str(path))
+    assert cfg._cfg == values
+    return str(path)
+
+
+def test_fixture_holds_every_shipped_config():
+    assert CONFIGS == [f"configs/test/{n}shot_split{s}.py" for n in (1, 5) for s in range(1, 6)]
+    assert TRAIN == [f"configs/train/{n}shot_split{s}.py" for n in (1, 5) for s in range(1, 6)]
+
+
+@pytest.mark.parametrize("rel", CONFIGS, ids=CONFIGS)
+def test_reference_config_builds_unchanged(rel, tmp_path):
     from edgecape_amd import Config, build_posenet
     from edgecape_amd.detector import EdgeCape
-    cfg = Config.fromfile(path)
+    cfg = Config.fromfile(_config_file(rel, tmp_path))
     assert cfg.model.type == "EdgeCape" and cfg.model.keypoint_head.type == "TwoStageHead"
     model = build_posenet(cfg.model)                      # POSENETS -> HEADS -> TRANSFORMER / POSITIONAL_ENCODING registries
     assert isinstance(model, EdgeCape)
@@ -36,13 +63,13 @@ def test_reference_config_builds_unchanged(path):
     assert big.pretrained == "dinov2_vitb14" and big.keypoint_head_module.skeleton_head.dim_feedforward == 768
 
 
-@pytest.mark.parametrize("path", TRAIN, ids=[os.path.relpath(p, REF) for p in TRAIN])
-def test_train_configs_build_their_inference_model(path):
+@pytest.mark.parametrize("rel", TRAIN, ids=TRAIN)
+def test_train_configs_build_their_inference_model(rel, tmp_path):
     """Training is out of scope, evaluating a checkpoint of any training stage is not: the train configs describe the
     stage-1 model of run.py:44-101 (SkeletonPredictor(learn_skeleton=False), decoder self-attention without the Markov bias) and
     build unchanged (round 5; rounds 1-4 refused them); train() itself is refused."""
     from edgecape_amd import Config, build_posenet
-    cfg = Config.fromfile(path)
+    cfg = Config.fromfile(_config_file(rel, tmp_path))
     assert cfg.model.type == "EdgeCape" and "optimizer" in cfg
     model = build_posenet(cfg.model)
     th, sk = model.keypoint_head_module.transformer, model.keypoint_head_module.skeleton_head

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd $R
-B="python bench.py --precision $MODE --head-precision bf16x3 --no-cpu-baseline --no-alt --sustained-seconds 0 --steps 10"
+B="python bench.py --full --precision $MODE --head-precision bf16x3 --no-cpu-baseline --no-alt --sustained-seconds 0 --steps 10"
 $B > $OUT/x2_cfg2.json 2>> $OUT/bench.err
 $B --shots 5 --batch 16 > $OUT/x2_cfg4_5shot_b16.json 2>> $OUT/bench.err
 $B --arch dinov2_vitl14 --image-size 384 --batch 8 --no-episode > $OUT/x2_cfg5_vitl_384_b8.json 2>> $OUT/bench.err

@@ -10,7 +10,7 @@ cd $R
 prof_leg () {   # name, last steps, bench arguments...
   local name=$1 steps=$2; shift 2
   cd /tmp && export TMPDIR=/tmp
-  rocprofv3 --kernel-trace --stats -d $OUT/prof_$name -o r -- python $R/bench.py --no-cpu-baseline --no-alt --sustained-seconds 0 "$@" > $OUT/prof_${name}.json 2> $OUT/prof_${name}.err
+  rocprofv3 --kernel-trace --stats -d $OUT/prof_$name -o r -- python $R/bench.py --full --no-cpu-baseline --no-alt --sustained-seconds 0 "$@" > $OUT/prof_${name}.json 2> $OUT/prof_${name}.err
   cd $R
   local DB=$(ls $OUT/prof_$name/*/*results.db $OUT/prof_$name/*results.db 2>/dev/null | head -1)
   python tools/rocpd_stats.py $DB $OUT/kernel_stats_${name}.csv $steps
