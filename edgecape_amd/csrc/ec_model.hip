@@ -2499,6 +2499,8 @@ int ec_op_linear(const float* A, const float* W, const float* bias, const float*
   GemmP p;
   p.M = M; p.N = N; p.K = K; p.lda = K; p.ldb = K; p.ldc = N; p.C = C; p.bias = bias; p.gamma = gamma; p.resid = resid; p.ldr = N;
   p.act = act;
+  EC_REQUIRE(precision == EC_F32 || precision == EC_BF16 || precision == EC_F16 || precision == EC_BF16X3 || precision == EC_MIXED,
+             EC_ERR_ARG, "ec_op_linear: precision must be EC_F32, EC_BF16, EC_F16, EC_BF16X3 or EC_MIXED (EC_F16X2: ec_op_linear_x2)");
   if (precision == EC_BF16 || precision == EC_F16) {
     const int f16 = precision == EC_F16;
     bf16_t *a16 = nullptr, *w16 = nullptr;
@@ -2695,6 +2697,8 @@ int ec_op_chain(const float* X, int K1, const float* W1, const float* b1, const 
 
 int ec_op_attention(const float* q, const float* k, const float* v, const uint8_t* kmask, const float* bias, float* o, int B, int H,
                     int Lq, int Lk, int hd, int precision, void* stream) {
+  EC_REQUIRE(precision == EC_F32 || precision == EC_BF16 || precision == EC_F16 || precision == EC_BF16X3, EC_ERR_ARG,
+             "ec_op_attention: precision must be EC_F32, EC_BF16, EC_F16 or EC_BF16X3 (the other forms: ec_op_attention_ex)");
   if (precision == EC_BF16 || precision == EC_F16) {
     // test path: round q,k,v to the 16-bit format on device, run the 16-bit kernel, widen the result
     const int f16 = precision == EC_F16;
@@ -2735,6 +2739,41 @@ int ec_op_attention(const float* q, const float* k, const float* v, const uint8_
   a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.hd = hd;
   a.split = precision == EC_BF16X3;
   return attention(a, (hipStream_t)stream);
+}
+
+int ec_op_attention_ex(const void* q, const void* k, const void* v, void* o, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo,
+                       int64_t sQ, int64_t sK, int64_t sV, int64_t sO, const uint8_t* kmask, int mask_start, int mask_len, int mask_mod,
+                       const float* bias, int B, int H, int Lq, int Lk, int hd, int mode, int kv16, int o_x3, void* stream) {
+  EC_REQUIRE(mode == EC_F32 || mode == EC_BF16 || mode == EC_F16 || mode == EC_BF16X3 || mode == EC_MIXED, EC_ERR_ARG,
+             "ec_op_attention_ex: mode must be EC_F32, EC_BF16, EC_F16, EC_BF16X3 or EC_MIXED");
+  EC_REQUIRE(mode == EC_BF16X3 || mode == EC_MIXED || (!kv16 && !o_x3), EC_ERR_ARG, "ec_op_attention_ex: kv16 / o_x3 need a split mode");
+  EC_REQUIRE(o_x3 == 0 || o_x3 == 1 || o_x3 == 3, EC_ERR_ARG, "ec_op_attention_ex: o_x3 must be 0, 1 or 3");
+  AttnP a;
+  a.Q = q; a.K = k; a.V = v; a.O = o;
+  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
+  a.sQ = sQ; a.sK = sK; a.sV = sV; a.sO = sO;
+  a.kmask = kmask; a.mask_start = mask_start; a.mask_len = mask_len; a.mask_mod = mask_mod;
+  a.bias = bias;
+  a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.hd = hd;
+  a.bf16 = mode == EC_BF16 || mode == EC_F16; a.f16 = mode == EC_F16;
+  a.split = mode == EC_BF16X3 || mode == EC_MIXED; a.one = mode == EC_MIXED;
+  a.kv16 = kv16 ? 1 : 0; a.o_x3 = o_x3;
+  return attention(a, (hipStream_t)stream);
+}
+
+int ec_op_layernorm_ex(const float* x, int64_t ldx, void* y, int64_t ldy, int out_fmt, const float* w, const float* b, int rows, int cols,
+                       float eps, int drop_period, const void* add, const void* add2, int64_t ldadd, int add_fmt, float* xsum, void* y2,
+                       int64_t ldy2, void* stream) {
+  EC_REQUIRE(out_fmt == 0 || out_fmt == 1 || out_fmt == 2 || out_fmt == 3 || out_fmt == 6, EC_ERR_ARG,
+             "ec_op_layernorm_ex: out_fmt must be 0, 1, 2, 3 or 6");
+  EC_REQUIRE(!y2 || out_fmt == 0, EC_ERR_ARG, "ec_op_layernorm_ex: the fp16 side copy y2 exists beside fp32 output only");
+  LnP p;
+  p.x = x; p.ldx = ldx; p.y = y; p.ldy = ldy; p.y_bf16 = out_fmt;
+  p.w = w; p.b = b; p.rows = rows; p.cols = cols; p.eps = eps;
+  p.drop_period = drop_period;
+  p.add = add; p.add2 = add2; p.ldadd = ldadd; p.add_fmt = add_fmt; p.xsum = xsum;
+  p.y2 = y2; p.ldy2 = ldy2;
+  return layernorm(p, (hipStream_t)stream);
 }
 
 }  // extern "C"

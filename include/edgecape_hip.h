@@ -126,7 +126,7 @@ typedef struct ec_outputs {
 const char* ec_last_error(void);
 /* ABI version of the library (EC_ABI_VERSION of the header it was built from): bumped whenever a struct layout, an enum value, the set of entry points
    or a signature changes, so a binding can refuse a stale prebuilt library instead of calling it with mismatched layouts. */
-#define EC_ABI_VERSION 6   /* 6 (round 6): ec_precision EC_F16X2, ec_op_linear_x2 */
+#define EC_ABI_VERSION 7   /* 6 (round 6): ec_precision EC_F16X2, ec_op_linear_x2; 7: ec_op_attention_ex, ec_op_layernorm_ex */
 int ec_version(void);
 /* sizeof(ec_config) / sizeof(ec_outputs) as the library was compiled: a binding compares them with its own mirrors. */
 int ec_abi_sizes(int* config_bytes, int* outputs_bytes);
@@ -257,7 +257,8 @@ int ec_profile_read(ec_handle h, float* total_ms, int* launches);
 
 /* ---- single ops (parity tests / microbenchmarks) -------------------------------------------- */
 /* C[M,N] = epilogue(A[M,K] @ W[N,K]^T): precision EC_F32 -> fp32 operands, EC_BF16 -> operands are
- * rounded to bf16 on device first (EC_MIXED: the single-pass fp16 form of the mixed head precision).  act: 0 none, 1 relu, 2 gelu(erf).  bias/gamma/resid may be NULL. */
+ * rounded to bf16 on device first (EC_MIXED: the single-pass fp16 form of the mixed head precision).  act: 0 none, 1 relu, 2 gelu(erf).  bias/gamma/resid may be NULL.
+ * EC_F16X2 (ec_op_linear_x2) or an unknown precision is EC_ERR_ARG. */
 int ec_op_linear(const float* A_dev, const float* W_dev, const float* bias_dev, const float* gamma_dev,
                  const float* resid_dev, float* C_dev, int M, int N, int K, int act, int precision, void* stream);
 /* The block GEMMs of the backbone as the model runs them: operands rounded to the 16-bit format of `precision` (EC_BF16 / EC_F16) on
@@ -285,6 +286,16 @@ int ec_op_gemm_bench(const void* A_dev, const void* W_dev, const float* bias_dev
 int ec_op_bgemm(const float* A_dev, const float* B_dev, float* C_dev, int batch, int M, int N, int K, int transB, void* stream);
 int ec_op_layernorm(const float* x_dev, const float* w_dev, const float* b_dev, float* y_dev, int rows, int cols,
                     float eps, void* stream);
+/* LayerNorm with every form the model launches (the fields of ec_ops.h LnP as plain arguments), straight to the kernel dispatch:
+ *   y = LayerNorm(x') * w + b over `cols`, x' = x, or (x + add) + add2 in fp32 when add is set (16-bit branch rows of stride ldadd in
+ *   add_fmt's format: 1 bf16, 2 fp16, 0 = the output's); x' is written to xsum when xsum is not NULL (xsum may be x, same stride ldx).
+ *   out_fmt: 0 fp32, 1 bf16, 2 fp16 (saturated at +-65504), 3 bf16 split [hi | lo] (planes cols apart, ldy >= 2 cols, no add),
+ *   6 fp16x2 row [fp16 | e5m2 lo8 | e5m2 hi8] (ldy >= 2 cols 16-bit units, no add).  drop_period > 0: input row n * P + t goes to output
+ *   row n * (P - 1) + t - 1, rows t = 0 are dropped.  y2 (fp32 output only, may be NULL): an fp16 copy of y, row stride ldy2.
+ *   Strides in elements of the buffer's type; cols % 4 == 0, cols <= 1024. */
+int ec_op_layernorm_ex(const float* x_dev, int64_t ldx, void* y_dev, int64_t ldy, int out_fmt, const float* w_dev, const float* b_dev,
+                       int rows, int cols, float eps, int drop_period, const void* add_dev, const void* add2_dev, int64_t ldadd,
+                       int add_fmt, float* xsum_dev, void* y2_dev, int64_t ldy2, void* stream);
 /* Row-chain kernel of the head (ec_chain.hip; bf16x3 arithmetic), up to three stages over `rows` token rows in ONE launch:
  *     x1   = LayerNorm_1(resid + X @ W1^T + b1)                              X [rows,K1], W1 [256,K1]  -> x1_out [rows,256]
  *     out2 = act2([x1 | cat] @ W2^T + b2 + table[row % period])              W2 [N2, 256 + Kcat]       -> out2 [rows,N2]
@@ -299,10 +310,27 @@ int ec_op_chain(const float* X_dev, int K1, const float* W1_dev, const float* b1
                 int N2, int act2, const float* table_dev, int period, float* out2_dev, const float* W3_dev, const float* b3_dev,
                 const float* ln3_w_dev, const float* ln3_b_dev, float* x3_out_dev, int rows, int precision, void* stream);
 /* softmax(q k^T * hd^-0.5 + bias, key mask) v ; q [B,Lq,H*hd], k,v [B,Lk,H*hd]; kmask [B,Lk] uint8 (1 = masked) or NULL;
- * bias [B,H,Lq,Lk] or NULL. */
+ * bias [B,H,Lq,Lk] or NULL.  precision EC_F32, EC_BF16X3, or EC_BF16 / EC_F16 (fp32 data rounded on device, hd = 64, no mask / bias);
+ * any other value is EC_ERR_ARG. */
 int ec_op_attention(const float* q_dev, const float* k_dev, const float* v_dev, const uint8_t* kmask_dev,
                     const float* bias_dev, float* o_dev, int B, int H, int Lq, int Lk, int hd, int precision,
                     void* stream);
+/* The same attention with every field of the kernel's problem (ec_common.h AttnP) as the model passes it: operands as the caller's bytes
+ * (no conversion pass), row strides ld* and batch strides s* in elements of each operand's own type; head h of a row is the hd
+ * elements from h * hd.  Key k of batch b is masked when k >= mask_start and kmask[(mask_mod > 0 ? b % mask_mod : b) * mask_len +
+ * k - mask_start] != 0 (kmask may be NULL); bias [B,H,Lq,Lk] fp32 or NULL.
+ *   mode EC_F32:    fp32 Q/K/V/O, exact fp32 products
+ *   mode EC_BF16X3: fp32 Q/K/V/O, each product as three bf16 MFMAs (split)
+ *   mode EC_MIXED:  the split kernel's single-pass fp16 form (Q * hd^-0.5, K, V and P rounded to fp16, one fp16 MFMA per product)
+ *   mode EC_BF16 / EC_F16: Q/K/V/O all 16-bit (backbone kernel: hd = 64, no mask / bias)
+ *   kv16 (split modes, hd = 64): K and V are IEEE fp16.
+ *   o_x3 (split modes): 0 fp32 O; 1 bf16 split rows [hi | lo] (planes H * hd apart, ldo / sO in 16-bit units);
+ *        3 fp16x2 rows [fp16 | e5m2 lo8 | e5m2 hi8] (ldo / sO in 16-bit units, ldo >= 2 H hd).
+ * Apart from the mode and flag values, validates nothing beyond what the kernel dispatch itself enforces. */
+int ec_op_attention_ex(const void* q_dev, const void* k_dev, const void* v_dev, void* o_dev, int64_t ldq, int64_t ldk, int64_t ldv,
+                       int64_t ldo, int64_t sQ, int64_t sK, int64_t sV, int64_t sO, const uint8_t* kmask_dev, int mask_start,
+                       int mask_len, int mask_mod, const float* bias_dev, int B, int H, int Lq, int Lk, int hd, int mode, int kv16,
+                       int o_x3, void* stream);
 
 #ifdef __cplusplus
 }
